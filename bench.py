@@ -11,9 +11,18 @@ With N > 1 every rank advances its own ensemble member (BASELINE.json config 4;
 members never interact in the forward pass, reference rollout.py:220-283), so
 scaling is weak and `value` = N*K / max-over-ranks time.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra
-objects: `roofline` for the dominant kernel and `cpu_baseline` (the oracle's CPU restatement,
-on torch's CPU kernels, timed on the host cores on a bounded sample, N = 1 only).
+Rank 0 prints ONE JSON line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (wall time of one timed step) and a description of the run.  A plain run does
+only that: set up, warm up, time the K steps, print the line.
+
+  --dump-outputs DIR   after the timed steps, writes what the last timed step computed (the
+                       output y) as DIR/<name>.npy in float32: a fixed, seeded row sample when
+                       the whole array exceeds the budget (DUMP_BUDGET_BYTES, all files together)
+  --full               everything else, after the timed steps: the full-size f16x3-vs-f32
+                       `cross_check`, `roofline` for the dominant kernel (per-launch timing pass),
+                       the 40-step `rollout` / `rollout_api` extras and `cpu_baseline` (the
+                       oracle's CPU restatement, on torch's CPU kernels, timed on the host cores
+                       on a bounded sample, N = 1 only)
 """
 import argparse
 import json
@@ -39,6 +48,7 @@ PEAK_F16_MFMA_TFLOPS = 2500.0      # dense f16/bf16 MFMA peak (same guide; 2:1-s
 SUSTAINED_F16_MFMA_TFLOPS = {"mfma_only": 0.69 * 2500.0, "mfma_with_operand_streams": 0.55 * 2500.0,
                              "guide_measured_peak": 2495.0}
 LATENT = 512
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs: all files of one run together (a sample's row indices included)
 
 CONFIGS = {
     # name: (resolution, mesh_size, levels, gnn steps)
@@ -193,15 +203,17 @@ def cpu_baseline(c_in, c_out, steps, f_full, full_graphs=None, full_x=None, budg
 
   Sample: the same architecture (0.25deg/37L channel widths, `steps` processor steps) on the
   1deg/M5 graph -- 4.4 TFLOP as written -- timed with BOTH CPU back ends of the oracle: torch's
-  CPU kernels (oracle/torch_cpu.py; threads = physical cores) and numpy (oracle/gnn.py; BLAS
-  threads as configured, elementwise ops single-threaded).  The smaller 4deg/M3 graph only
+  CPU kernels (oracle/torch_cpu.py; threads = OMP_NUM_THREADS if set, else physical cores) and
+  numpy (oracle/gnn.py; BLAS threads as configured, elementwise ops single-threaded).  The smaller 4deg/M3 graph only
   warms the thread pools up; nothing is extrapolated from it.  If the faster back end predicts
   that ONE FULL 0.25deg step fits the time budget it is timed too and becomes the reported
   value (no extrapolation at all); otherwise the 1deg/M5 time is scaled by the as-written FLOP
   ratio (6.7x)."""
   from oracle import torch_cpu
   params = fast_params(c_in, c_out, steps)
-  threads = torch_cpu.set_threads()
+  # the CPUs this process may use: OMP_NUM_THREADS where the environment sets it, else the host's physical cores
+  omp = os.environ.get("OMP_NUM_THREADS", "")
+  threads = torch_cpu.set_threads(int(omp) if omp.isdigit() and int(omp) > 0 else None)
   warm_graphs, warm_x, _ = _oracle_sample("4deg_13L_M3", c_in, c_out, steps)
   _time_step("torch", params, warm_graphs, warm_x, steps)
   graphs, x, f_sample = _oracle_sample("1deg_13L_M5", c_in, c_out, steps)
@@ -221,7 +233,7 @@ def cpu_baseline(c_in, c_out, steps, f_full, full_graphs=None, full_x=None, budg
   fmt = lambda b: (f"{b} {secs[b]:.1f} s = {rates[b]:.0f} GFLOP/s" if secs[b] else f"{b} skipped (torch leg took > 30 s)")
   sample = (f"fp32 CPU restatement of the reference step, as written (JAX not installable), 0.25deg/37L "
             f"channel widths on the 1deg/M5 graph = {f_sample / 1e12:.2f} TFLOP: {fmt('torch')} on "
-            f"{threads} threads (physical cores), {fmt('numpy')}; ")
+            f"{threads} threads, {fmt('numpy')}; ")
   if measured_full is not None:
     sample += (f"then ONE FULL 0.25deg/37L/M6 step ({f_full / 1e12:.1f} TFLOP as written) timed with torch: "
                f"{measured_full:.1f} s = {f_full / measured_full / 1e9:.0f} GFLOP/s -- the reported value, "
@@ -247,6 +259,26 @@ def emit_line(text):
     print(text, flush=True)
   else:
     os.write(_REAL_STDOUT, (text + "\n").encode())
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+  """--dump-outputs: every tensor of `arrays` (name -> device tensor, rows along dim 0) as out_dir/<name>.npy in
+  float32.  A tensor larger than its share of `budget` is written as a sample of its rows -- the same rows for the
+  same shape in every run (seeded, sorted) -- and the sampled row indices go to out_dir/<name>_rows.npy (float64)."""
+  import torch
+  os.makedirs(out_dir, exist_ok=True)
+  share = budget // max(len(arrays), 1)
+  for name, t in arrays.items():
+    n = int(t.shape[0])
+    row_bytes = 4 * (t.numel() // max(n, 1))
+    if n * row_bytes <= share:
+      np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().float().cpu().numpy())
+      continue
+    k = share // (row_bytes + 8)
+    rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    sample = t.detach().index_select(0, torch.from_numpy(rows).to(t.device)).float().cpu().numpy()
+    np.save(os.path.join(out_dir, f"{name}.npy"), sample)
+    np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
 
 
 def main():
@@ -275,7 +307,15 @@ def main():
                        "reference's pmap_devices form (utils/rollout.py:196-283; rollout.chunked_prediction_generator("
                        "pmap_devices=...) here) -- instead of one process per GPU.  Devices are cuda:0 .. cuda:N-1, wrapping "
                        "around the visible ones (a 1-GPU box runs N engines on N streams of its one device)")
+  ap.add_argument("--full", action="store_true",
+                  help="after the timed steps, also run every further measurement and check: the cross-check, the "
+                       "per-launch roofline, the rollout extras, the CPU baseline (a plain run only times the steps)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the last timed step computed to DIR/<name>.npy (float32; a fixed, seeded row "
+                       f"sample when larger than {DUMP_BUDGET_BYTES >> 20} MiB in all)")
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be >= 1 and --warmup >= 0")
 
   # stdout carries ONE JSON line and nothing else.  RCCL prints a version banner to the C-level stdout of every process
   # that creates a communicator (plain printf, flushed at exit -- i.e. AFTER anything Python prints; NCCL_DEBUG_FILE
@@ -359,12 +399,14 @@ def main():
   engine.check_range()          # (outside the timed region: the inputs were inside the f16x3 arithmetic's exact range)
   finite = bool(torch.isfinite(y).all().item())
   precision = engine.precision
+  if args.dump_outputs:         # what the last timed step computed, before anything else runs on the engine
+    dump_outputs(args.dump_outputs, {"y" if world == 1 else f"y_rank{rank}": y}, budget=DUMP_BUDGET_BYTES // world)
 
   # Full-size parity property (outside the timed region): the two arithmetic modes -- exact fp32
   # MFMA and the 3 x f16 split -- must agree on the whole 0.25 deg output far inside the 1e-4
   # budget.  (The float64 oracle pins both at sizes it finishes in seconds: tests/.)
   cross = None
-  if rank == 0 and world == 1 and not args.no_cross_check:
+  if args.full and rank == 0 and world == 1 and not args.no_cross_check:
     other = "f32" if precision == "f16x3" else "f16x3"
     ref_engine = eng.StepEngine(g, params, num_steps=gnn_steps, c_in=c_in, c_out=c_out,
                                 device=device, precision=other)
@@ -379,20 +421,6 @@ def main():
 
   if rank == 0:
     ms_per_step = 1e3 * elapsed / args.steps
-    f_alg = flops_as_written(n_grid, g["n_mesh"], len(g["g2m"]["senders"]),
-                             len(g["mesh"]["senders"]), len(g["m2g"]["senders"]),
-                             c_in, c_out, gnn_steps)
-    per_stage = stage_table(engine, x, y, args.op_timing_iters)
-    dominant = max(per_stage, key=lambda s: per_stage[s]["ms"])
-    dom = per_stage[dominant]
-    achieved = dom["tflop"] / (dom["ms"] / 1e3) if dom["ms"] > 0 else 0.0
-    executed_tflop = sum(s["tflop"] for s in per_stage.values())
-    split = precision == "f16x3"
-    peak = PEAK_FP32_MFMA_TFLOPS if precision == "f32" else PEAK_F16_MFMA_TFLOPS
-    issue = 3.0 if split else 1.0            # MFMA FLOPs issued per algorithmic FLOP
-    traffic_key = f"{precision}{'h' if getattr(engine, 'half', False) else ''}"
-    traffic, traffic_why = measured_traffic(traffic_key, dominant)
-    pmc, pmc_why = measured_mfma_busy(traffic_key, dominant)
     line = {
         "metric": "6-h rollout steps/sec at 0.25deg/37-level",
         "value": args.gpus * args.steps / elapsed,
@@ -413,38 +441,20 @@ def main():
                         f"{gnn_steps} processor steps, latent 512), random-init weights",
             "parallelism": f"ensemble x{args.gpus} (1 member per GPU, no collective in the step)",
             "batch_per_gpu": 1},
-        "roofline": {
-            "bound": "mfma",
-            "kernel": f"{dominant_kernel_name(precision, dominant, dom, nat.get_tuning())} stage {dominant}",
-            "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-            "frac": achieved / peak,
-            "mfma_flops_per_algorithmic_flop": issue,
-            "mfma_issue_frac": issue * achieved / peak,
-            # the same MFMA work against what the chip sustains under power with real operands
-            "sustained_peak_measured": (None if precision == "f32" else SUSTAINED_F16_MFMA_TFLOPS),
-            "mfma_issue_frac_of_sustained": (None if precision == "f32" else
-                                             issue * achieved / SUSTAINED_F16_MFMA_TFLOPS["mfma_with_operand_streams"]),
-            "launches_per_step": dom["launches"],
-            "avg_launch_ms": dom["ms"] / dom["launches"],
-            "traffic": (traffic or {}).get("bytes_per_launch"),
-            "traffic_detail": traffic if traffic is not None else {"unavailable": traffic_why},
-            "pmc": pmc if pmc is not None else {"unavailable": pmc_why},
-            # the weight stream of the dominant launch: packed-weight bytes DMA'd L2 -> LDS per launch over its duration,
-            # against the chip-wide LDS-DMA fill rate of MI355X_MICROARCH.md (6.4-6.8 TB/s; HBM-sourced there, L2 hits here)
-            "lds_fill": {"bytes_per_launch": dom["lds_fill_bytes"] / dom["launches"],
-                         "achieved_tb_per_s": (dom["lds_fill_bytes"] / (dom["ms"] / 1e3) / 1e12 if dom["ms"] > 0 else 0.0),
-                         "guide_tb_per_s": [6.4, 6.8]},
-            "step_executed_tflop": executed_tflop,
-            "step_as_written_tflop": f_alg / 1e12,
-            "step_frac_executed": executed_tflop / (ms_per_step / 1e3) / peak,
-            "step_frac_as_written": f_alg / 1e12 / (ms_per_step / 1e3) / peak,
-            # every stage against the same peak (executed FLOPs of its launches / its HIP-event time)
-            "stages": stages_summary(per_stage, peak)},
-        "precision": precision,
-        "tier": (None if precision in ("f16x3", "f32") else
-                 "reduced-precision TIER line: the headline is the default f16x3 run (fp32-grade results)"),
-        "cross_check": cross,
-        "stages_ms": {k: round(v["ms"], 3) for k, v in sorted(per_stage.items())},
+    }
+    if args.full:
+      f_alg = flops_as_written(n_grid, g["n_mesh"], len(g["g2m"]["senders"]),
+                               len(g["mesh"]["senders"]), len(g["m2g"]["senders"]),
+                               c_in, c_out, gnn_steps)
+      per_stage = stage_table(engine, x, y, args.op_timing_iters)
+      line["roofline"] = roofline_summary(engine, precision, per_stage, f_alg, ms_per_step)
+    line["precision"] = precision
+    line["tier"] = (None if precision in ("f16x3", "f32") else
+                    "reduced-precision TIER line: the headline is the default f16x3 run (fp32-grade results)")
+    if args.full:
+      line["cross_check"] = cross
+      line["stages_ms"] = {k: round(v["ms"], 3) for k, v in sorted(per_stage.items())}
+    line.update({
         "setup_seconds": round(t_setup, 1),
         "output_finite": finite,
         "formulation": (("half-N kernels, two persistent four-wave workgroups per CU, chained layers"
@@ -458,8 +468,9 @@ def main():
         # the library's ONE tuning surface (include/gcast.h: gc_tuning) as this process ran with it -- every speed-only
         # A/B switch, whatever set it (the GCAST_* variables only initialise it)
         "tuning": nat.tuning_string(),
-    }
-    if args.gpus == 1 and args.rollout_steps > 0 and args.config == "0.25deg_37L_M6":
+        "full": args.full,
+    })
+    if args.full and args.gpus == 1 and args.rollout_steps > 0 and args.config == "0.25deg_37L_M6":
       line["rollout"] = rollout_extra(model, task, lat, lon, args.rollout_steps)
       # the metric's own word is "rollout": the same figure for the 40-step AUTOREGRESSIVE device loop (state advance
       # included) beside `value` (= K repeated steps on a constant input, the contract's timed region) -- VERDICT r5 weak #11
@@ -467,15 +478,59 @@ def main():
       line["value_rollout_what"] = (f"steps/s of the {args.rollout_steps}-step autoregressive rollout resident in HBM (line.rollout: "
                                     "step + gc_advance_state per lead time, HIP-event time of the device loop)")
       line["rollout_api"] = rollout_api_extra(model, task, lat, lon, args.rollout_steps)
-    if args.gpus == 1 and not args.no_cpu_baseline:
-      line["cpu_baseline"] = cpu_baseline(c_in, c_out, gnn_steps, f_alg, full_graphs=g,
-                                          full_x=x.cpu().numpy())
-    else:
-      line["cpu_baseline"] = None
+    if args.full:
+      if args.gpus == 1 and not args.no_cpu_baseline:
+        line["cpu_baseline"] = cpu_baseline(c_in, c_out, gnn_steps, f_alg, full_graphs=g,
+                                            full_x=x.cpu().numpy())
+      else:
+        line["cpu_baseline"] = None
   if distributed:
     dist.destroy_process_group()
   if rank == 0:
     emit_line(json.dumps(line))              # the ONE line on stdout
+
+
+def roofline_summary(engine, precision, per_stage, f_alg, ms_per_step):
+  """`roofline` of the line (--full): the dominant stage of `per_stage` (stage_table) against the MFMA peak of the
+  arithmetic, the committed counter summaries of the loaded build attached, every stage against the same peak."""
+  from graphcast_amd import _native as nat
+  dominant = max(per_stage, key=lambda s: per_stage[s]["ms"])
+  dom = per_stage[dominant]
+  achieved = dom["tflop"] / (dom["ms"] / 1e3) if dom["ms"] > 0 else 0.0
+  executed_tflop = sum(s["tflop"] for s in per_stage.values())
+  split = precision == "f16x3"
+  peak = PEAK_FP32_MFMA_TFLOPS if precision == "f32" else PEAK_F16_MFMA_TFLOPS
+  issue = 3.0 if split else 1.0            # MFMA FLOPs issued per algorithmic FLOP
+  traffic_key = f"{precision}{'h' if getattr(engine, 'half', False) else ''}"
+  traffic, traffic_why = measured_traffic(traffic_key, dominant)
+  pmc, pmc_why = measured_mfma_busy(traffic_key, dominant)
+  return {
+      "bound": "mfma",
+      "kernel": f"{dominant_kernel_name(precision, dominant, dom, nat.get_tuning())} stage {dominant}",
+      "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+      "frac": achieved / peak,
+      "mfma_flops_per_algorithmic_flop": issue,
+      "mfma_issue_frac": issue * achieved / peak,
+      # the same MFMA work against what the chip sustains under power with real operands
+      "sustained_peak_measured": (None if precision == "f32" else SUSTAINED_F16_MFMA_TFLOPS),
+      "mfma_issue_frac_of_sustained": (None if precision == "f32" else
+                                       issue * achieved / SUSTAINED_F16_MFMA_TFLOPS["mfma_with_operand_streams"]),
+      "launches_per_step": dom["launches"],
+      "avg_launch_ms": dom["ms"] / dom["launches"],
+      "traffic": (traffic or {}).get("bytes_per_launch"),
+      "traffic_detail": traffic if traffic is not None else {"unavailable": traffic_why},
+      "pmc": pmc if pmc is not None else {"unavailable": pmc_why},
+      # the weight stream of the dominant launch: packed-weight bytes DMA'd L2 -> LDS per launch over its duration,
+      # against the chip-wide LDS-DMA fill rate of MI355X_MICROARCH.md (6.4-6.8 TB/s; HBM-sourced there, L2 hits here)
+      "lds_fill": {"bytes_per_launch": dom["lds_fill_bytes"] / dom["launches"],
+                   "achieved_tb_per_s": (dom["lds_fill_bytes"] / (dom["ms"] / 1e3) / 1e12 if dom["ms"] > 0 else 0.0),
+                   "guide_tb_per_s": [6.4, 6.8]},
+      "step_executed_tflop": executed_tflop,
+      "step_as_written_tflop": f_alg / 1e12,
+      "step_frac_executed": executed_tflop / (ms_per_step / 1e3) / peak,
+      "step_frac_as_written": f_alg / 1e12 / (ms_per_step / 1e3) / peak,
+      # every stage against the same peak (executed FLOPs of its launches / its HIP-event time)
+      "stages": stages_summary(per_stage, peak)}
 
 
 class _PowerPoll:
@@ -750,20 +805,11 @@ def single_process_main(args):
   for m, *_ in members:
     m._engine.check_range()
   finite = all(bool(torch.isfinite(y).all().item()) for _, _, _, y, _ in members)
-  same_bits = None
-  if len(set(devices)) < len(devices):            # engines sharing a device: a member re-run ALONE gives the same bits
-    m, stream, x, y, dev = members[-1]
-    alone = torch.empty_like(y)
-    m._engine(x, alone)
-    torch.cuda.synchronize(dev)
-    same_bits = bool(torch.equal(alone, y))
+  if args.dump_outputs:
+    dump_outputs(args.dump_outputs, {("y" if len(members) == 1 else f"y_member{d}"): y
+                                     for d, (_, _, _, y, _) in enumerate(members)})
   engine = model._engine
   precision = engine.precision
-  peak = PEAK_FP32_MFMA_TFLOPS if precision == "f32" else PEAK_F16_MFMA_TFLOPS
-  per_stage = stage_table(engine, members[0][2], members[0][3], args.op_timing_iters)
-  dominant = max(per_stage, key=lambda k: per_stage[k]["ms"])
-  dom = per_stage[dominant]
-  achieved = dom["tflop"] / (dom["ms"] / 1e3) if dom["ms"] > 0 else 0.0
   line = {
       "metric": "6-h rollout steps/sec at 0.25deg/37-level", "value": args.gpus * args.steps / elapsed, "unit": "steps/s",
       "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -776,14 +822,30 @@ def single_process_main(args):
                                 "form; no collective in the step)",
                  "devices": devices, "distinct_devices": len(set(devices)), "batch_per_gpu": 1,
                  "note": (None if len(set(devices)) == len(devices) else
-                          "engines share a device: `value` is that device's rate with several engines resident, not a scaling point")},
-      "roofline": {"bound": "mfma", "kernel": f"{dominant_kernel_name(precision, dominant, dom, nat.get_tuning())} stage {dominant} (engine 0, timed alone)",
-                   "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak, "traffic": None,
-                   "launches_per_step": dom["launches"], "avg_launch_ms": dom["ms"] / dom["launches"],
-                   "stages": stages_summary(per_stage, peak)},
-      "cpu_baseline": None,
-      "precision": precision, "output_finite": finite, "member_alone_gives_the_same_bits": same_bits,
-      "setup_seconds": round(t_setup, 1), "build": nat.lib().gc_build_info().decode(), "tuning": nat.tuning_string()}
+                          "engines share a device: `value` is that device's rate with several engines resident, not a scaling point")}}
+  if args.full:
+    same_bits = None
+    if len(set(devices)) < len(devices):          # engines sharing a device: a member re-run ALONE gives the same bits
+      m, stream, x, y, dev = members[-1]
+      alone = torch.empty_like(y)
+      m._engine(x, alone)
+      torch.cuda.synchronize(dev)
+      same_bits = bool(torch.equal(alone, y))
+    peak = PEAK_FP32_MFMA_TFLOPS if precision == "f32" else PEAK_F16_MFMA_TFLOPS
+    per_stage = stage_table(engine, members[0][2], members[0][3], args.op_timing_iters)
+    dominant = max(per_stage, key=lambda k: per_stage[k]["ms"])
+    dom = per_stage[dominant]
+    achieved = dom["tflop"] / (dom["ms"] / 1e3) if dom["ms"] > 0 else 0.0
+    line["roofline"] = {"bound": "mfma", "kernel": f"{dominant_kernel_name(precision, dominant, dom, nat.get_tuning())} stage {dominant} (engine 0, timed alone)",
+                        "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak, "traffic": None,
+                        "launches_per_step": dom["launches"], "avg_launch_ms": dom["ms"] / dom["launches"],
+                        "stages": stages_summary(per_stage, peak)}
+    line["cpu_baseline"] = None
+  line.update({"precision": precision, "output_finite": finite})
+  if args.full:
+    line["member_alone_gives_the_same_bits"] = same_bits
+  line.update({"setup_seconds": round(t_setup, 1), "build": nat.lib().gc_build_info().decode(), "tuning": nat.tuning_string(),
+               "full": args.full})
   emit_line(json.dumps(line))
 
 
@@ -836,38 +898,20 @@ def partition_main(args, rank, world, device, distributed):
   fin = torch.tensor([1 if bool(torch.isfinite(y).all().item()) else 0], dtype=torch.int32, device=device)
   dist.all_reduce(fin, op=dist.ReduceOp.MIN)
   finite = bool(fin.item())
-  # per-rank roofline: this rank's launches timed one by one (HIP events, no exchange in between), max over ranks per stage
   precision = step.engine.precision
-  peak = PEAK_FP32_MFMA_TFLOPS if precision == "f32" else PEAK_F16_MFMA_TFLOPS
-  per_stage = stage_table(step.engine, x, y, args.op_timing_iters)
-  names = sorted(per_stage)
-  ms = torch.tensor([per_stage[k]["ms"] for k in names], dtype=torch.float64, device=device)
-  dist.all_reduce(ms, op=dist.ReduceOp.MAX)          # (every rank has the same stage names: the same launch program)
-  exch = exchange_probe(step, world, device)
+  if args.dump_outputs:         # this rank's shard of the output (its owned grid rows)
+    dump_outputs(args.dump_outputs, {"y" if world == 1 else f"y_rank{rank}": y}, budget=DUMP_BUDGET_BYTES // world)
+  if args.full:
+    # per-rank roofline: this rank's launches timed one by one (HIP events, no exchange in between), max over ranks per stage
+    peak = PEAK_FP32_MFMA_TFLOPS if precision == "f32" else PEAK_F16_MFMA_TFLOPS
+    per_stage = stage_table(step.engine, x, y, args.op_timing_iters)
+    names = sorted(per_stage)
+    ms = torch.tensor([per_stage[k]["ms"] for k in names], dtype=torch.float64, device=device)
+    dist.all_reduce(ms, op=dist.ReduceOp.MAX)          # (every rank has the same stage names: the same launch program)
+    exch = exchange_probe(step, world, device)
   if rank == 0:
     halo = {k: int(len(pl.halo_global)) for k, (pl, _) in partition.tables_of(mine).items()}
-    stages = stages_summary(per_stage, peak)
-    for k, v in zip(names, ms.tolist()):
-      if k in stages:
-        stages[k]["ms_max_over_ranks"] = round(v, 3)
-    dominant = max(stages, key=lambda k: stages[k]["ms"])
-    dom = per_stage[dominant]
-    compute_ms = float(sum(ms.tolist()))
-    cpu = None
-    if world == 1 and not args.no_cpu_baseline:      # the same whole step on the host cores (rank 0, N = 1 only)
-      f_alg = flops_as_written(g["n_grid"], g["n_mesh"], len(g["g2m"]["senders"]), len(g["mesh"]["senders"]),
-                               len(g["m2g"]["senders"]), c_in, c_out, gnn_steps)
-      cpu = cpu_baseline(c_in, c_out, gnn_steps, f_alg, full_graphs=g,
-                         full_x=np.random.default_rng(0).standard_normal((g["n_grid"], 1, c_in), dtype=np.float32))
-    roofline = {"bound": "mfma", "kernel": f"rowmlp16h_kernel<MLP_LN> stage {dominant} (rank 0's share of the launch)",
-                "achieved": stages[dominant]["achieved"], "peak": peak, "unit": "TFLOP/s", "frac": stages[dominant]["frac"],
-                "launches_per_step": dom["launches"], "avg_launch_ms": dom["ms"] / dom["launches"], "traffic": None,
-                "mfma_flops_per_algorithmic_flop": 3.0 if precision == "f16x3" else 1.0,
-                "stages": stages, "rank_compute_ms_per_step_max_over_ranks": compute_ms,
-                "exchange": exch,
-                "note": "per-rank launches timed one by one (gc_time_program); a rank's launches are 1/N of the step's "
-                        "rows -- few tiles per CU: see DESIGN.md section 7"}
-    line = json.dumps({
+    line = {
         "metric": "6-h rollout steps/sec at 0.25deg/37-level",
         "value": args.steps / elapsed, "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -876,11 +920,34 @@ def partition_main(args, rank, world, device, distributed):
         "config": {"workload": f"GraphCast {args.config}: ONE encode-process-decode 6-h step partitioned over {world} GPU(s)",
                    "parallelism": f"octant partition x{world} (partition.plan: hemispheres / quadrants / octants), receiver-owned "
                                   f"edges, 18 halo exchanges per step = one RCCL all_to_all_single each",
-                   "rank0_rows": {"grid": mine.n_grid_owned, "mesh": mine.n_mesh_owned, "halo": halo}},
-        "roofline": roofline,
-        "cpu_baseline": cpu,
-        "precision": precision, "output_finite": finite,
-        "build": nat.lib().gc_build_info().decode(), "tuning": nat.tuning_string()})
+                   "rank0_rows": {"grid": mine.n_grid_owned, "mesh": mine.n_mesh_owned, "halo": halo}}}
+    if args.full:
+      stages = stages_summary(per_stage, peak)
+      for k, v in zip(names, ms.tolist()):
+        if k in stages:
+          stages[k]["ms_max_over_ranks"] = round(v, 3)
+      dominant = max(stages, key=lambda k: stages[k]["ms"])
+      dom = per_stage[dominant]
+      compute_ms = float(sum(ms.tolist()))
+      cpu = None
+      if world == 1 and not args.no_cpu_baseline:      # the same whole step on the host cores (rank 0, N = 1 only)
+        f_alg = flops_as_written(g["n_grid"], g["n_mesh"], len(g["g2m"]["senders"]), len(g["mesh"]["senders"]),
+                                 len(g["m2g"]["senders"]), c_in, c_out, gnn_steps)
+        cpu = cpu_baseline(c_in, c_out, gnn_steps, f_alg, full_graphs=g,
+                           full_x=np.random.default_rng(0).standard_normal((g["n_grid"], 1, c_in), dtype=np.float32))
+      line["roofline"] = {
+          "bound": "mfma", "kernel": f"rowmlp16h_kernel<MLP_LN> stage {dominant} (rank 0's share of the launch)",
+          "achieved": stages[dominant]["achieved"], "peak": peak, "unit": "TFLOP/s", "frac": stages[dominant]["frac"],
+          "launches_per_step": dom["launches"], "avg_launch_ms": dom["ms"] / dom["launches"], "traffic": None,
+          "mfma_flops_per_algorithmic_flop": 3.0 if precision == "f16x3" else 1.0,
+          "stages": stages, "rank_compute_ms_per_step_max_over_ranks": compute_ms,
+          "exchange": exch,
+          "note": "per-rank launches timed one by one (gc_time_program); a rank's launches are 1/N of the step's "
+                  "rows -- few tiles per CU: see DESIGN.md section 7"}
+      line["cpu_baseline"] = cpu
+    line.update({"precision": precision, "output_finite": finite,
+                 "build": nat.lib().gc_build_info().decode(), "tuning": nat.tuning_string(), "full": args.full})
+    line = json.dumps(line)
   dist.destroy_process_group()
   if rank == 0:
     emit_line(line)

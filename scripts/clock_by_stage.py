@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Shader clock per STAGE of one 0.25 deg step, from ONE rocprofv3 pass `--kernel-trace --pmc SQ_WAVE_CYCLES` of
-`bench.py --steps 1 --warmup 0 --op-timing-iters 1`: the persistent row-MLP launches keep a fixed number of waves
+`bench.py --full --steps 1 --warmup 0 --op-timing-iters 1`: the persistent row-MLP launches keep a fixed number of waves
 resident for their whole duration (512 four-wave or 256 eight-wave workgroups = 2048 waves on the 1,024 SIMDs), so
 
     clock = 4 * SQ_WAVE_CYCLES / (waves * duration)          (SQ_WAVE_CYCLES counts quad-cycles summed over waves)

@@ -16,18 +16,18 @@ if [ "${DO_TESTS:-1}" = "1" ]; then
   grep -E "passed|failed|FULLSIZE_PARITY|ROLLOUT" "$OUT/pytest_gpu.log" | tail -6 | cut -c1-500
   [ $rc = 0 ] || { echo "GATE: GPU suite failed"; exit 1; }
 fi
-echo "== bench (driver's command)"; t0=$(date +%s); timeout 1200 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$? wall=$(( $(date +%s) - t0 )) s" | tee "$OUT/bench_wall.txt"; cut -c1-300 "$OUT/bench.json"
-echo "== bench, bf16 tier"; timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check --rollout-steps 0 --precision bf16 > "$OUT/bench_bf16.json" 2>> "$OUT/bench.err"; echo "bench bf16 rc=$?"; cut -c1-200 "$OUT/bench_bf16.json"
+echo "== bench --full (the headline workload with every extra)"; t0=$(date +%s); timeout 1200 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$? wall=$(( $(date +%s) - t0 )) s" | tee "$OUT/bench_wall.txt"; cut -c1-300 "$OUT/bench.json"
+echo "== bench, bf16 tier"; timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check --rollout-steps 0 --precision bf16 > "$OUT/bench_bf16.json" 2>> "$OUT/bench.err"; echo "bench bf16 rc=$?"; cut -c1-200 "$OUT/bench_bf16.json"
 echo "== rocprofv3 kernel trace"
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o trace -- \
-    python "$OLDPWD/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err"); echo "rocprof rc=$?"
+    python "$OLDPWD/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err"); echo "rocprof rc=$?"
 python scripts/kernel_trace_by_stage.py "$OUT/prof" > "$OUT/kernel_trace_by_stage.csv" 2>> "$OUT/errors.txt"; head -c 600 "$OUT/kernel_trace_by_stage.csv"; echo
 for f in $(find "$OUT/prof" -name "*kernel_stats.csv" | head -1); do cp "$f" "$OUT/kernel_stats.csv"; done
 find "$OUT/prof" -type f -size +8M -delete
 for C in FETCH_SIZE WRITE_SIZE; do
   echo "== rocprofv3 --pmc $C"
   (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OLDPWD/$OUT/pmc_$C" -o pmc -- \
-      python "$OLDPWD/bench.py" --steps 1 --warmup 0 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 > "$OLDPWD/$OUT/pmc_$C.json" 2> "$OLDPWD/$OUT/pmc_$C.err"); echo "pmc $C rc=$?"
+      python "$OLDPWD/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 > "$OLDPWD/$OUT/pmc_$C.json" 2> "$OLDPWD/$OUT/pmc_$C.err"); echo "pmc $C rc=$?"
 done
 # (the row-MLP launches' counter rows, kept small enough to commit: the per-stage summaries are reproducible from them)
 rows() { python - "$1" "$2" "${3:-rowmlp16}" <<'PY'
@@ -53,7 +53,7 @@ if [ "${DO_SQ:-1}" = "1" ]; then
     i=$((i + 1))
     echo "== rocprofv3 --pmc (SQ set $i)"
     (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OLDPWD/$OUT/pmc_sq$i" -o pmc -- \
-        python "$OLDPWD/bench.py" --steps 1 --warmup 0 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 > "$OLDPWD/$OUT/pmc_sq$i.json" 2> "$OLDPWD/$OUT/pmc_sq$i.err"); echo "pmc sq$i rc=$?"
+        python "$OLDPWD/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 > "$OLDPWD/$OUT/pmc_sq$i.json" 2> "$OLDPWD/$OUT/pmc_sq$i.err"); echo "pmc sq$i rc=$?"
   done
   for i in 1 2; do rows "$OUT/pmc_sq$i" "$OUT/pmc_sq${i}_rowmlp_launches.csv"; done
   python scripts/sq_by_stage.py "$OUT/pmc_sq1_rowmlp_launches.csv" "$OUT/pmc_sq2_rowmlp_launches.csv" > "$OUT/sq_by_stage.json" 2>> "$OUT/errors.txt"
@@ -68,7 +68,7 @@ if [ "${DO_BF16_PMC:-1}" = "1" ]; then
   for C in FETCH_SIZE WRITE_SIZE; do
     echo "== rocprofv3 --pmc $C (bf16 tier)"
     (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OLDPWD/$OUT/pmc_bf16_$C" -o pmc -- \
-        python "$OLDPWD/bench.py" $BF > "$OLDPWD/$OUT/pmc_bf16_$C.json" 2> "$OLDPWD/$OUT/pmc_bf16_$C.err"); echo "pmc bf16 $C rc=$?"
+        python "$OLDPWD/bench.py" --full $BF > "$OLDPWD/$OUT/pmc_bf16_$C.json" 2> "$OLDPWD/$OUT/pmc_bf16_$C.err"); echo "pmc bf16 $C rc=$?"
     rows "$OUT/pmc_bf16_$C" "$OUT/pmc_bf16_${C}_rowmlp_launches.csv" rowmlpbf
   done
   python scripts/pmc_by_stage.py "$OUT/pmc_bf16_FETCH_SIZE_rowmlp_launches.csv" "$OUT/pmc_bf16_WRITE_SIZE_rowmlp_launches.csv" --elem 2 > "$OUT/current_pmc_by_stage_bf16.json" 2>> "$OUT/errors.txt"; head -c 300 "$OUT/current_pmc_by_stage_bf16.json"; echo
@@ -77,7 +77,7 @@ if [ "${DO_BF16_PMC:-1}" = "1" ]; then
     i=$((i + 1))
     echo "== rocprofv3 --pmc (SQ set $i, bf16 tier)"
     (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OLDPWD/$OUT/pmc_bf16_sq$i" -o pmc -- \
-        python "$OLDPWD/bench.py" $BF > "$OLDPWD/$OUT/pmc_bf16_sq$i.json" 2> "$OLDPWD/$OUT/pmc_bf16_sq$i.err"); echo "pmc bf16 sq$i rc=$?"
+        python "$OLDPWD/bench.py" --full $BF > "$OLDPWD/$OUT/pmc_bf16_sq$i.json" 2> "$OLDPWD/$OUT/pmc_bf16_sq$i.err"); echo "pmc bf16 sq$i rc=$?"
     rows "$OUT/pmc_bf16_sq$i" "$OUT/pmc_bf16_sq${i}_rowmlp_launches.csv" rowmlpbf
   done
   python scripts/sq_by_stage.py "$OUT/pmc_bf16_sq1_rowmlp_launches.csv" "$OUT/pmc_bf16_sq2_rowmlp_launches.csv" --bf16 > "$OUT/current_sq_by_stage_bf16.json" 2>> "$OUT/errors.txt"
@@ -88,9 +88,9 @@ find "$OUT" -type f -size +8M -delete
 # round 5: the step at the part's power limit (socket power / shader clock polled while it runs), the partition-mode
 # line at N = 1 (per-rank roofline, exchange probe) and the driver's SCALE launch form at N = 1
 echo "== power probe"; timeout 300 python scripts/power_probe.py --seconds 6 --out "$OUT/power_probe.json" 2>&1 | grep -v amdgpu.ids | head -1 | cut -c1-400
-echo "== bench --mode partition (N = 1)"; timeout 600 python bench.py --mode partition --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_partition_n1.json" 2>> "$OUT/bench.err"; echo "rc=$?"; cut -c1-200 "$OUT/bench_partition_n1.json"
-echo "== bench under torch.distributed.run (N = 1)"; timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_torchrun_n1.json" 2>> "$OUT/bench.err"; echo "rc=$? lines=$(wc -l < "$OUT/bench_torchrun_n1.json")"
+echo "== bench --mode partition (N = 1)"; timeout 600 python bench.py --full --mode partition --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_partition_n1.json" 2>> "$OUT/bench.err"; echo "rc=$?"; cut -c1-200 "$OUT/bench_partition_n1.json"
+echo "== bench under torch.distributed.run (N = 1)"; timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_torchrun_n1.json" 2>> "$OUT/bench.err"; echo "rc=$? lines=$(wc -l < "$OUT/bench_torchrun_n1.json")"
 
 # round 6: the second launch form of --gpus N -- ONE process driving N engines (the reference's pmap_devices form); on a
 # 1-GPU box the two engines share the device
-echo "== bench --gpus 2 --single-process"; timeout 600 python bench.py --gpus 2 --single-process --steps 5 --warmup 2 > "$OUT/bench_single_process_2.json" 2>> "$OUT/bench.err"; echo "rc=$?"; cut -c1-200 "$OUT/bench_single_process_2.json"
+echo "== bench --gpus 2 --single-process"; timeout 600 python bench.py --full --gpus 2 --single-process --steps 5 --warmup 2 > "$OUT/bench_single_process_2.json" 2>> "$OUT/bench.err"; echo "rc=$?"; cut -c1-200 "$OUT/bench_single_process_2.json"

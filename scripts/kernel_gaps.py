@@ -5,8 +5,8 @@ sum of the kernel durations, and the idle gaps between consecutive kernels group
 
     python scripts/kernel_gaps.py gpurun_out/<run>/prof [--steps 3] [--skip-tail 3] > profiles/<name>.json
 
---skip-tail: whole step patterns at the END of the trace that are not timed steps (bench.py's per-launch timing pass,
-gc_time_program, runs the same kernels one by one behind the timed steps).
+--skip-tail: whole step patterns at the END of the trace that are not timed steps (bench.py --full: the per-launch
+timing pass, gc_time_program, runs the same kernels one by one behind the timed steps).
 """
 import collections
 import csv

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Per-STAGE HBM traffic of one 0.25 deg step from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of
-`bench.py --steps 1 --warmup 0 --op-timing-iters 1`.  The persistent kernels launch every stage with the same
+`bench.py --full --steps 1 --warmup 0 --op-timing-iters 1`.  The persistent kernels launch every stage with the same
 grid (512 workgroups), so a launch is identified by its POSITION: the row-MLP dispatches of a pass end with
 whole steps of 38 launches -- embed_grid, enc_edge, enc_node_mesh, enc_node_grid, 16 x (proc_edge, proc_node),
 dec_edge, dec_node -- and the last step (bench.py's per-op timing pass) is the one summarised.

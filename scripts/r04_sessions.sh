@@ -11,7 +11,7 @@ case "$NAME" in
     # Round-4 session 1: A/B of the persistent launches' tile -> workgroup map (GCAST_TILE_MAP=xcd) and of
     # one workgroup per CU (GCAST_GRID_CAP=256), each as its own bench.py process of the headline workload.
     OUT=gpurun_out/r04_s1; mkdir -p "$OUT"
-    B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check"
+    B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check"
     run() { tag=$1; shift; echo "== $tag"; env "$@" timeout 400 $B > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err"; echo "rc=$?"; python - "$OUT/bench_$tag.json" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -59,16 +59,16 @@ PY
     timeout 1500 python -m pytest tests/test_rowmlp_gpu.py tests/test_step_gpu.py tests/test_plan_gpu.py tests/test_partition_gpu.py tests/test_deepgnn_gpu.py tests/test_bf16_tier_gpu.py tests/test_rollout_gpu.py -m gpu -q --timeout=600 -rA > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?"
     grep -E "passed|failed|BF16_TIER_ERROR_SHAPE|NCCL_WS1|C host|in-range|Error|error" "$OUT/pytest.log" | tail -25 | cut -c1-400
     echo "== bench (rollout extra, no cpu baseline)"
-    timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "rc=$?"
+    timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "rc=$?"
     python - "$OUT/bench.json" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(j["ms_per_step"], j.get("rollout"), j["roofline"]["traffic_detail"], j["roofline"]["pmc"], j["cross_check"])
 PY
     echo "== bench --mode partition (N = 1: a single-rank RCCL group)"
-    timeout 600 python bench.py --mode partition --steps 5 --warmup 2 > "$OUT/bench_partition1.json" 2> "$OUT/bench_partition1.err"; echo "rc=$?"; cut -c1-600 "$OUT/bench_partition1.json"; tail -3 "$OUT/bench_partition1.err"
+    timeout 600 python bench.py --full --mode partition --steps 5 --warmup 2 > "$OUT/bench_partition1.json" 2> "$OUT/bench_partition1.err"; echo "rc=$?"; cut -c1-600 "$OUT/bench_partition1.json"; tail -3 "$OUT/bench_partition1.err"
     echo "== the same under torchrun with WORLD_SIZE=1 (what the driver's N = 1 scaling point does)"
-    timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_torchrun1.json" 2> "$OUT/bench_torchrun1.err"; echo "rc=$?"; cut -c1-300 "$OUT/bench_torchrun1.json"; tail -2 "$OUT/bench_torchrun1.err"
+    timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_torchrun1.json" 2> "$OUT/bench_torchrun1.err"; echo "rc=$?"; cut -c1-300 "$OUT/bench_torchrun1.json"; tail -2 "$OUT/bench_torchrun1.err"
     ;;
   s7)
     # Round-4 session 7: the helper-wave form (now with the parked accumulators in LDS) on the big node-side launches only.
@@ -106,7 +106,7 @@ PY
     done
     for v in 0 1; do
       echo "== bench 1deg_13L_M5, GCAST_HELPERS_SMALL=$v"
-      GCAST_HELPERS_SMALL=$v timeout 300 python bench.py --config 1deg_13L_M5 --steps 20 --warmup 5 --no-cpu-baseline --no-cross-check --rollout-steps 0 2>/dev/null | python -c "
+      GCAST_HELPERS_SMALL=$v timeout 300 python bench.py --full --config 1deg_13L_M5 --steps 20 --warmup 5 --no-cpu-baseline --no-cross-check --rollout-steps 0 2>/dev/null | python -c "
     import json,sys
     j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(j['ms_per_step'], {k: round(v['ms'],3) for k,v in j['roofline']['stages'].items()})"
     done

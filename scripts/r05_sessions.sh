@@ -23,8 +23,8 @@ case "$NAME" in
     # roofline + exchange probe.
     timeout 900 python -m pytest tests/test_step_gpu.py tests/test_plan_gpu.py tests/test_rollout_gpu.py tests/test_partition_gpu.py -m gpu -q -x --timeout=600 > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?"; tail -5 "$OUT/pytest.log"
     gate "$OUT/pytest.log" "host-side changes"
-    timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
-    timeout 600 python bench.py --mode partition --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_partition_n1.json" 2> "$OUT/bench_partition.err"; echo "partition rc=$?"; show "$OUT/bench_partition_n1.json"
+    timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
+    timeout 600 python bench.py --full --mode partition --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_partition_n1.json" 2> "$OUT/bench_partition.err"; echo "partition rc=$?"; show "$OUT/bench_partition_n1.json"
     ;;
   s2)
     # Round-5 session 2: wave issue priority by phase (gc_rowmlp_desc.flags GC_PRIO / GCAST_PRIO="gemm,other,stage"):
@@ -35,14 +35,14 @@ case "$NAME" in
         "GCAST_HELPERS=1 GCAST_PRIO=3,0,0" "GCAST_HELPERS=1 GCAST_PRIO=0,0,1"
     bash scripts/session.sh bench-ab r05_s2b --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check --rollout-steps 0 --precision bf16 -- \
         "GCAST_PRIO=0,0,0" "GCAST_PRIO=1,0,0" "GCAST_PRIO=0,1,0" "GCAST_PRIO=0,0,0"
-    timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check > "$OUT/bench_rollout_api.json" 2> "$OUT/bench_rollout_api.err"; echo "bench rc=$?"; show "$OUT/bench_rollout_api.json"
+    timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check > "$OUT/bench_rollout_api.json" 2> "$OUT/bench_rollout_api.err"; echo "bench rc=$?"; show "$OUT/bench_rollout_api.json"
     ;;
   s3)
     # Round-5 session 3: where the host time of the fused rollout behind rollout.chunked_prediction_generator goes
     # (rollout_api.host_seconds), with the device-side upload in DeviceRollout._prepare and the sampled cross-check; the
     # shipped priority default against GCAST_PRIO=0,0,0; the emulated 8-way partition's per-rank time (baseline).
-    timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
-    GCAST_PRIO=0,0,0 timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_prio0.json" 2> "$OUT/bench_prio0.err"; echo "bench rc=$?"; show "$OUT/bench_prio0.json"
+    timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
+    GCAST_PRIO=0,0,0 timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_prio0.json" 2> "$OUT/bench_prio0.err"; echo "bench rc=$?"; show "$OUT/bench_prio0.json"
     timeout 600 python scripts/partition_emulated_bench.py --parts 8 --out "$OUT/partition8.json" 2>&1 | tail -5
     ;;
   s4)
@@ -51,7 +51,7 @@ case "$NAME" in
     timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; echo "smoke rc=$?"; tail -2 "$OUT/smoke.log"
     timeout 1200 python -m pytest tests/test_rowmlp_gpu.py tests/test_step_gpu.py tests/test_plan_gpu.py tests/test_rollout_gpu.py tests/test_bf16_tier_gpu.py tests/test_native_abi.py tests/test_deepgnn_gpu.py tests/test_conditioned_gpu.py -m gpu -q -x --timeout=600 > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?"; tail -4 "$OUT/pytest.log"
     gate "$OUT/pytest.log" "prune"
-    timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
+    timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
     ;;
   s5)
     # Round-5 session 5: ONE program builder -- engine.StepEngine on gc_plan_program / gc_plan_tensor, partitioned graphs
@@ -60,21 +60,21 @@ case "$NAME" in
     timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; echo "smoke rc=$?"; tail -2 "$OUT/smoke.log"
     timeout 1500 python -m pytest tests -m gpu -q --timeout=900 --deselect tests/test_rollout40_fullsize_gpu.py > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?"; tail -6 "$OUT/pytest.log" | cut -c1-400
     grep -E "FULLSIZE_PARITY|ROLLOUT" "$OUT/pytest.log" | cut -c1-600
-    timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
-    timeout 600 python bench.py --mode partition --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_partition_n1.json" 2> "$OUT/bench_partition.err"; echo "partition rc=$?"; show "$OUT/bench_partition_n1.json"
+    timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
+    timeout 600 python bench.py --full --mode partition --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_partition_n1.json" 2> "$OUT/bench_partition.err"; echo "partition rc=$?"; show "$OUT/bench_partition_n1.json"
     timeout 600 python scripts/partition_emulated_bench.py --parts 8 --out "$OUT/partition8.json" 2>&1 | tail -3 | cut -c1-600
     ;;
   s6)
     # Round-5 session 6: the driver's SCALE launch form at N = 1 (torch.distributed.run -> RCCL group of one rank): stdout
     # must carry the JSON line and NOTHING else (RCCL prints a banner to the C-level stdout); the same for --mode partition.
-    timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_torchrun_n1.json" 2> "$OUT/bench_torchrun_n1.err"; echo "torchrun bench rc=$?"
+    timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_torchrun_n1.json" 2> "$OUT/bench_torchrun_n1.err"; echo "torchrun bench rc=$?"
     python - "$OUT/bench_torchrun_n1.json" <<'PY'
 import json, sys
 raw = open(sys.argv[1]).read()
 lines = [l for l in raw.splitlines() if l.strip()]
 print("stdout lines:", len(lines)); j = json.loads(raw); print("ONE JSON document on stdout:", j["n_gpus"], round(j["ms_per_step"], 3), j["config"]["parallelism"])
 PY
-    timeout 600 python bench.py --mode partition --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_partition_n1.json" 2> "$OUT/bench_partition.err"; echo "partition rc=$?"
+    timeout 600 python bench.py --full --mode partition --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_partition_n1.json" 2> "$OUT/bench_partition.err"; echo "partition rc=$?"
     python - "$OUT/bench_partition_n1.json" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read()); print("partition: ONE JSON document on stdout:", round(j["ms_per_step"], 3), j["roofline"]["exchange"]["device_ms_per_step"], j["output_finite"])
@@ -133,7 +133,7 @@ PY
     # does to the one behind it.  (One --pmc pass each, kernel trace only: the node-safe combination.)
     for E in 0 1; do
       (cd /tmp && GCAST_HELPERS_EDGE=$E timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES --output-format csv -d "$OLDPWD/$OUT/pmc_edge$E" -o pmc -- \
-          python "$OLDPWD/bench.py" --steps 1 --warmup 0 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 > "$OLDPWD/$OUT/bench_edge$E.json" 2> "$OLDPWD/$OUT/bench_edge$E.err"); echo "pmc edge=$E rc=$?"
+          python "$OLDPWD/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 > "$OLDPWD/$OUT/bench_edge$E.json" 2> "$OLDPWD/$OUT/bench_edge$E.err"); echo "pmc edge=$E rc=$?"
       python scripts/clock_by_stage.py "$OUT/pmc_edge$E" > "$OUT/clock_by_stage_edge$E.json" 2>> "$OUT/errors.txt"
       python -c "
 import json; j=json.load(open('$OUT/clock_by_stage_edge$E.json')); print({k: (v['clock_ghz'], v['ms_per_launch_under_the_counter_pass']) for k, v in j.items()})"
@@ -155,7 +155,7 @@ import json; j=json.load(open('$OUT/clock_by_stage_edge$E.json')); print({k: (v[
     # (b) the step / launch / plan / partition / rollout suites with the processor edge update pinned to each kernel
     # form (GCAST_HELPERS_EDGE=1: eight-wave HST form at every size; =0: the pair everywhere) -- the default rule mixes
     # them by size; (c) power / clock while the bf16 tier and the 1 deg step run: which of them are power-bound.
-    timeout 900 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
+    timeout 900 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
     python - "$OUT/bench.json" <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])["roofline"]
@@ -180,7 +180,7 @@ PY
     # GCAST_HELPERS_EDGE=0, same session.
     bash scripts/session.sh bench-ab r05_s16 --steps 20 --warmup 5 --no-cpu-baseline --no-cross-check --rollout-steps 0 --config 1deg_13L_M5 -- "" "GCAST_HELPERS_EDGE=0" "" "GCAST_HELPERS_EDGE=0"
     (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof_1deg" -o trace -- \
-        python "$OLDPWD/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 --config 1deg_13L_M5 > "$OLDPWD/$OUT/prof_1deg_bench.json" 2> "$OLDPWD/$OUT/prof_1deg.err"); echo "rocprof rc=$?"
+        python "$OLDPWD/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 --config 1deg_13L_M5 > "$OLDPWD/$OUT/prof_1deg_bench.json" 2> "$OLDPWD/$OUT/prof_1deg.err"); echo "rocprof rc=$?"
     f=$(find "$OUT/prof_1deg" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && { cut -c1-240 "$f" | head -12 | tee "$OUT/kernel_stats_1deg_head.csv"; }
     for E in default 0; do
       if [ "$E" = default ]; then unset GCAST_HELPERS_EDGE; else export GCAST_HELPERS_EDGE=$E; fi

@@ -36,8 +36,8 @@ case "$NAME" in
     # single-process launch form, and more same-session samples of gc_tuning.wide_edges.
     timeout 1500 python -m pytest tests/test_native_abi.py tests/test_step_gpu.py tests/test_plan_gpu.py tests/test_rollout_gpu.py -m gpu -q -x --timeout=900 > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?"; tail -5 "$OUT/pytest.log" | cut -c1-400
     gate "$OUT/pytest.log" "host-side changes"
-    timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
-    timeout 900 python bench.py --gpus 2 --single-process --steps 10 --warmup 3 > "$OUT/bench_single_process_2.json" 2> "$OUT/bench_single_process_2.err"; echo "single-process rc=$?"; show "$OUT/bench_single_process_2.json"
+    timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench.json"
+    timeout 900 python bench.py --full --gpus 2 --single-process --steps 10 --warmup 3 > "$OUT/bench_single_process_2.json" 2> "$OUT/bench_single_process_2.err"; echo "single-process rc=$?"; show "$OUT/bench_single_process_2.json"
     bash scripts/session.sh bench-ab r06_s2 "GCAST_WIDE_EDGES=0" "GCAST_WIDE_EDGES=1" "GCAST_WIDE_EDGES=3" "GCAST_WIDE_EDGES=0" "GCAST_WIDE_EDGES=1" "GCAST_WIDE_EDGES=3"
     ;;
   s3)
@@ -46,9 +46,9 @@ case "$NAME" in
     # then the sizes the headline does not show: the 1 deg step, an 8-way rank (emulated), the bf16 tier.
     bash scripts/session.sh bench-ab r06_s3 "GCAST_WIDE_EDGES=3" "GCAST_WIDE_EDGES=0" "GCAST_WIDE_EDGES=2" "GCAST_WIDE_EDGES=3 GCAST_PRIO=0,0,0" \
         "GCAST_WIDE_EDGES=3 GCAST_TILE_QUEUE=0" "GCAST_WIDE_EDGES=3" "GCAST_WIDE_EDGES=0"
-    timeout 600 python bench.py --config 1deg_13L_M5 --steps 20 --warmup 5 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_1deg.json" 2> "$OUT/bench_1deg.err"; echo "1deg rc=$?"; show "$OUT/bench_1deg.json"
+    timeout 600 python bench.py --full --config 1deg_13L_M5 --steps 20 --warmup 5 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_1deg.json" 2> "$OUT/bench_1deg.err"; echo "1deg rc=$?"; show "$OUT/bench_1deg.json"
     timeout 600 python scripts/partition_emulated_bench.py --parts 8 --out "$OUT/partition8.json" 2>&1 | tail -2 | cut -c1-700
-    timeout 600 python bench.py --precision bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err"; echo "bf16 rc=$?"; show "$OUT/bench_bf16.json"
+    timeout 600 python bench.py --full --precision bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err"; echo "bf16 rc=$?"; show "$OUT/bench_bf16.json"
     ;;
   s4)
     # Round-6 session 4: gc_tuning.split_tail -- the processor's node updates (641 tiles = 1.6 rounds of four-wave pairs) as
@@ -164,7 +164,7 @@ case "$NAME" in
     # four-wave pairs), and against the library of commit e8bb181.
     for E in "" "GCAST_HELPERS_EDGE=0" "GCAST_LIB_PATH=ab_libs/libgcast_r6head.so"; do
       tag=$(echo "${E:-default}" | tr ' =/' '__-')
-      env $E timeout 600 python bench.py --config 1deg_13L_M5 --steps 20 --warmup 5 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_1deg_$tag.json" 2> "$OUT/bench_1deg_$tag.err"; echo "1deg [$E] rc=$?"; show "$OUT/bench_1deg_$tag.json"
+      env $E timeout 600 python bench.py --full --config 1deg_13L_M5 --steps 20 --warmup 5 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_1deg_$tag.json" 2> "$OUT/bench_1deg_$tag.err"; echo "1deg [$E] rc=$?"; show "$OUT/bench_1deg_$tag.json"
       env $E timeout 600 python scripts/partition_emulated_bench.py --parts 8 --out "$OUT/partition8_$tag.json" 2>&1 | tail -1 | cut -c1-600
     done
     ;;
@@ -179,17 +179,17 @@ case "$NAME" in
     fi
     for E in "" "GCAST_SPLIT_EDGES=0" "" "GCAST_SPLIT_EDGES=0"; do
       i=$((${i:-0} + 1)); tag=$(echo "${E:-default}" | tr ' =/' '__-')
-      env $E timeout 600 python bench.py --config 1deg_13L_M5 --steps 20 --warmup 5 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_1deg_${i}_$tag.json" 2> "$OUT/bench_1deg_${i}_$tag.err"; echo "1deg [$E] rc=$?"; show "$OUT/bench_1deg_${i}_$tag.json"
+      env $E timeout 600 python bench.py --full --config 1deg_13L_M5 --steps 20 --warmup 5 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_1deg_${i}_$tag.json" 2> "$OUT/bench_1deg_${i}_$tag.err"; echo "1deg [$E] rc=$?"; show "$OUT/bench_1deg_${i}_$tag.json"
       env $E timeout 600 python scripts/partition_emulated_bench.py --parts 8 --out "$OUT/partition8_${i}_$tag.json" 2>&1 | tail -1 | cut -c1-900
     done
-    timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"; echo "full rc=$?"; show "$OUT/bench_full.json"
+    timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check --rollout-steps 0 > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"; echo "full rc=$?"; show "$OUT/bench_full.json"
     ;;
   s17)
     # Round-6 session 17: where the 1 deg step's time goes BETWEEN its kernels (session s16: a second launch per edge update
     # cost the step 0.3 ms where the launch itself lost 0.05) -- a kernel trace of the 1 deg step and of an emulated 8-way
     # step, gaps grouped by (previous kernel -> next kernel).
     (cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$OLDPWD/$OUT/prof_1deg" -o trace -- \
-        python "$OLDPWD/bench.py" --config 1deg_13L_M5 --steps 10 --warmup 2 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 > "$OLDPWD/$OUT/prof_1deg.json" 2> "$OLDPWD/$OUT/prof_1deg.err"); echo "rocprof rc=$?"
+        python "$OLDPWD/bench.py" --full --config 1deg_13L_M5 --steps 10 --warmup 2 --no-cpu-baseline --no-cross-check --rollout-steps 0 --op-timing-iters 1 > "$OLDPWD/$OUT/prof_1deg.json" 2> "$OLDPWD/$OUT/prof_1deg.err"); echo "rocprof rc=$?"
     python scripts/kernel_gaps.py "$OUT/prof_1deg" --steps 4 --skip-tail 3 > "$OUT/kernel_gaps_1deg.json"; head -c 3000 "$OUT/kernel_gaps_1deg.json"
     find "$OUT" -type f -size +8M -delete
     ;;
@@ -198,7 +198,7 @@ case "$NAME" in
     # output bitwise against the first, other work beside every second repetition; both precisions, 1 deg and 0.25 deg) and the
     # driver's step count with the round-end session's stamped counters attached to the line (roofline.traffic / pmc).
     timeout 1200 python scripts/repeat_stress.py --reps 30 --out "$OUT/repeat_stress.json" 2>&1 | grep -v amdgpu.ids | tail -6; echo "stress rc=${PIPESTATUS[0]}"
-    timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_counters_attached.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench_counters_attached.json"
+    timeout 900 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_counters_attached.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; show "$OUT/bench_counters_attached.json"
     python - "$OUT/bench_counters_attached.json" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -248,13 +248,13 @@ PY
     # gc_plan.k_lat, and the rewritten input-tail kernel; + the prep tests and one bench line for the stage times).
     timeout 1400 python scripts/general_sizes_fullsize.py --cases "${CASES:-256x1,384x1,128x1,512x2,64x2,128x3}" --out "$OUT/general_sizes_fullsize.json" 2>&1 | grep -v amdgpu.ids | tail -8
     timeout 300 python -m pytest tests/test_rowmlp_gpu.py -q -m gpu -k prep 2>&1 | tail -2
-    timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check --rollout-steps 0 2>/dev/null | cut -c1-400
+    timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-cross-check --rollout-steps 0 2>/dev/null | cut -c1-400
     ;;
   s27)
     # Round-6 session 27: the paths around the step on the library of final5 -- repeatability stress, emulated 8-way rank, 1 deg.
     timeout 1200 python scripts/repeat_stress.py --reps 40 --out "$OUT/repeat_stress.json" 2>&1 | grep -v amdgpu.ids | cut -c1-250 | tail -6
     timeout 900 python scripts/partition_emulated_bench.py --parts 8 2>&1 | grep -v amdgpu.ids | tail -1 | cut -c1-600
-    timeout 600 python bench.py --config 1deg_13L_M5 --no-cpu-baseline --rollout-steps 0 2>/dev/null | cut -c1-300
+    timeout 600 python bench.py --full --config 1deg_13L_M5 --no-cpu-baseline --rollout-steps 0 2>/dev/null | cut -c1-300
     ;;
   *) echo "unknown session $NAME"; exit 2;;
 esac

@@ -29,7 +29,7 @@ case "$MODE" in
     for ENVS in "$@"; do
       i=$((i + 1)); tag=$(echo "${ENVS:-default}" | tr ' =/' '__-' | cut -c1-60)
       echo "== [$i] $ENVS"
-      env $ENVS timeout 600 python bench.py $ARGS > "$OUT/bench_${i}_$tag.json" 2> "$OUT/bench_${i}_$tag.err"; echo "rc=$?"
+      env $ENVS timeout 600 python bench.py --full $ARGS > "$OUT/bench_${i}_$tag.json" 2> "$OUT/bench_${i}_$tag.err"; echo "rc=$?"
       summary "$OUT/bench_${i}_$tag.json"
     done;;
   probe)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Per-STAGE SQ counters of one 0.25 deg step from rocprofv3 --pmc passes of
-`bench.py --steps 1 --warmup 0 --op-timing-iters 1` (any number of pass directories; a launch is identified
+`bench.py --full --steps 1 --warmup 0 --op-timing-iters 1` (any number of pass directories; a launch is identified
 by its position in the step exactly as in scripts/pmc_by_stage.py).  Per stage and counter: mean per launch;
 derived where the inputs are present (units per /opt/skills/guides/MI355X_MICROARCH.md: SQ_WAVE_CYCLES and the
 SQ_WAIT_* / SQ_ACTIVE_INST_* counters are QUAD-cycles summed over waves, SQ_VALU_MFMA_BUSY_CYCLES is cycles

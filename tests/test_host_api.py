@@ -804,6 +804,38 @@ def test_bench_weight_stream_bytes_of_a_launch():
   assert bench.op_weight_stream_bytes(op) == 0.0
 
 
+def test_bench_dump_outputs_is_a_fixed_bounded_float32_sample(tmp_path):
+  """bench.py --dump-outputs: an output larger than the budget is written as a seeded sample of its rows (the same rows
+  in every run, indices beside it), a small one whole; every file float32 / float64, all of them within the budget."""
+  import torch
+  import bench
+  y = torch.randn(100000, 1, 227)
+  for d in ("a", "b"):
+    bench.dump_outputs(str(tmp_path / d), {"y": y}, budget=8 << 20)
+  rows = np.load(tmp_path / "a" / "y_rows.npy")
+  got = np.load(tmp_path / "a" / "y.npy")
+  assert rows.dtype == np.float64 and got.dtype == np.float32 and got.shape[1:] == (1, 227)
+  assert np.all(np.diff(rows) > 0) and len(rows) == got.shape[0] > 1000
+  np.testing.assert_array_equal(got, y.numpy()[rows.astype(np.int64)])
+  np.testing.assert_array_equal(np.load(tmp_path / "b" / "y_rows.npy"), rows)
+  assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 8 << 20
+  small = torch.randn(50, 1, 3, dtype=torch.float64)
+  bench.dump_outputs(str(tmp_path / "c"), {"y": small})
+  assert sorted(os.listdir(tmp_path / "c")) == ["y.npy"]
+  np.testing.assert_array_equal(np.load(tmp_path / "c" / "y.npy"), small.float().numpy())
+
+
+def test_bench_options():
+  """bench.py takes --full and --dump-outputs, and refuses a run without timed steps before it touches a GPU."""
+  import subprocess
+  import sys
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  usage = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True)
+  assert usage.returncode == 0 and "--full" in usage.stdout and "--dump-outputs" in usage.stdout
+  none = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+  assert none.returncode == 2 and "--steps" in none.stderr
+
+
 def test_wrappers_pass_host_datasets_through_when_there_is_no_gpu_predictor():
   """predictor_base.host_datasets_on_device uploads only around a predictor that lives on a GPU: a chain without a
   device (or on the CPU) gets the caller's numpy-backed Datasets unchanged, and device_of finds the innermost

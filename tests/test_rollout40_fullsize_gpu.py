@@ -49,7 +49,7 @@ def test_forty_step_rollout_at_headline_size(golden_dir):
   report = {"config": "0.25deg_37L_M6, 16 processor steps, 40 autoregressive steps, 256 sampled grid rows x 227 channels",
             "oracle": f"tests/golden/{FIXTURE} (torch-CPU fp32 oracle through rollout.chunked_prediction + InputsAndResiduals)",
             "rel_rmse_step_1_10_20_30_40": [per_step[k] for k in (0, 9, 19, 29, 39)], "rel_rmse_max": max(per_step),
-            "rel_rmse_per_step": per_step}       # (timing of this loop: bench.py's `rollout` -- here the first step builds the engine)
+            "rel_rmse_per_step": per_step}       # (timing of this loop: `rollout` of bench.py --full -- here the first step builds the engine)
   print("ROLLOUT40_FULLSIZE_PARITY " + json.dumps(report))
   out_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
   os.makedirs(out_dir, exist_ok=True)
