@@ -134,7 +134,9 @@ class Tuning(ctypes.Structure):
 EXPORTS = ("gc_get_tuning", "gc_set_tuning", "gc_plan_get_tuning", "gc_tuning_string", "gc_plan_create", "gc_plan_workspace_bytes", "gc_step_forward", "gc_plan_check_range", "gc_plan_destroy",
            "gc_plan_program", "gc_plan_tensor",
            "gc_host_pack_weight", "gc_host_pack_edges", "gc_host_pad_latent", "gc_advance_state", "gc_rowmlp", "gc_seg_fixup", "gc_zero_rows", "gc_seg_fixup_bf16", "gc_zero_rows_bf16", "gc_add_rows", "gc_prep_grid_input", "gc_prep_grid_tail",
-           "gc_run_program", "gc_time_program", "gc_abi_sizeof", "gc_last_error", "gc_build_info")
+           "gc_run_program", "gc_time_program", "gc_abi_sizeof", "gc_last_error", "gc_build_info",
+           # GenCast's mesh transformer (csrc/attention.inc)
+           "gc_attention", "gc_ln_cond_rows", "gc_gelu_rows", "gc_permute_rows")
 
 
 # Build variants of the one source: "main" = the shipped library.  Further entries are A/B builds
@@ -165,6 +167,11 @@ RESOURCE_LIMITS = {"rowmlp16h_kernel": dict(scratch=160, occupancy=2), "rowmlpbf
                    # the wide form (eight multiplying waves, one workgroup per CU): the same budget again
                    # (round 6: + the late-addend instantiation of gc_tuning.wide_late)
                    "rowmlp16w_kernel": dict(scratch=200, occupancy=2)}
+
+
+# The mesh transformer's kernels (csrc/attention.inc): the attention tile kernel is built for TWO workgroups per CU
+# (67.6 / 71.8 KiB of LDS each) and must not spill.  Checked by build() with a dict of its own.
+ATTN_RESOURCE_LIMITS = {"attn_tile_kernel": dict(scratch=0, occupancy=2)}
 
 
 def check_resources(remarks, limits=None):
@@ -258,12 +265,13 @@ def build(force=False, verbose=False):
           print(line, file=sys.stderr)
     try:
       usage = check_resources(res.stderr)
+      usage.update(check_resources(res.stderr, ATTN_RESOURCE_LIMITS))
     except RuntimeError:
       os.remove(out)
       raise
     if verbose:
       for sym, u in sorted(usage.items()):
-        if any(k in sym for k in RESOURCE_LIMITS):
+        if any(k in sym for k in RESOURCE_LIMITS) or any(k in sym for k in ATTN_RESOURCE_LIMITS):
           print(f"  {sym}: {u}", file=sys.stderr)
 
 
@@ -334,6 +342,14 @@ def lib():
     l.gc_get_tuning.restype = l.gc_set_tuning.restype = l.gc_plan_get_tuning.restype = ctypes.c_int
     l.gc_tuning_string.argtypes = [ctypes.POINTER(Tuning)]
     l.gc_tuning_string.restype = ctypes.c_char_p
+    l.gc_attention.argtypes = [ctypes.c_int] * 4 + [_fp] * 6 + [ctypes.c_int, ctypes.c_float, _fp, ctypes.c_int, _fp,
+                                                               ctypes.c_void_p]
+    l.gc_ln_cond_rows.argtypes = [ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, ctypes.c_void_p]
+    l.gc_gelu_rows.argtypes = [ctypes.c_longlong, _fp, ctypes.c_void_p]
+    l.gc_permute_rows.argtypes = [ctypes.c_int, ctypes.c_int, _fp, _fp, ctypes.c_longlong, ctypes.c_int, _fp,
+                                  ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]
+    for name in ("gc_attention", "gc_ln_cond_rows", "gc_gelu_rows", "gc_permute_rows"):
+      getattr(l, name).restype = ctypes.c_int
     l.gc_last_error.restype = ctypes.c_char_p
     l.gc_abi_sizeof.argtypes = [ctypes.c_int]
     l.gc_abi_sizeof.restype = ctypes.c_size_t

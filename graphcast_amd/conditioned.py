@@ -17,7 +17,7 @@ bias).  Edge embeddings depend on the conditioning here, so nothing is constant-
 (GraphCast's engine folds them, engine.py); the first edge-MLP layer is still split per node
 ((x[idx]).W == (x.W)[idx]).
 
-The sparse-transformer processor between the two (``denoiser.py:331-339``) is out of scope.
+The sparse-transformer processor between the two (``denoiser.py:331-339``) is ``sparse_transformer.Transformer``.
 """
 from typing import Mapping, Optional
 

@@ -1509,3 +1509,5 @@ const char* gc_build_info(void) {
 }
 
 }  // extern "C"
+
+#include "attention.inc"

@@ -108,3 +108,24 @@ def faces_to_edges(faces: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
   """Each face (a, b, c) contributes a->b, b->c, c->a; senders = [a; b; c], receivers = [b; c; a]."""
   assert faces.ndim == 2 and faces.shape[-1] == 3
   return faces.T.reshape(-1), np.roll(faces, -1, axis=1).T.reshape(-1)
+
+
+def get_sparse_adjacency_matrix(mesh: TriangularMesh):
+  """scipy csr [V, V] with 1 at (sender, receiver) of every face edge (reference icosahedral_mesh.py:403-409)."""
+  from scipy import sparse
+  senders, receivers = faces_to_edges(mesh.faces)
+  n = mesh.vertices.shape[0]
+  adj = sparse.csr_matrix((np.ones(len(senders)), (senders, receivers)), shape=(n, n))
+  adj.sum_duplicates()
+  adj.data[:] = 1.0
+  return adj
+
+
+def get_permutation_to_banded(mesh: TriangularMesh):
+  """(permutation, permute_func) of reference icosahedral_mesh.py:412-423: the reverse Cuthill-McKee order of the
+  mesh graph (deterministic), and the map old vertex index -> new position.  GenCast numbers its mesh this way."""
+  from scipy.sparse import csgraph
+  permutation = csgraph.reverse_cuthill_mckee(get_sparse_adjacency_matrix(mesh), symmetric_mode=True)
+  position = np.empty(len(permutation), dtype=np.int64)
+  position[permutation] = np.arange(len(permutation))
+  return permutation, lambda x: position[np.asarray(x)]

@@ -572,6 +572,41 @@ const char* gc_tuning_string(const gc_tuning* t);
 #define GC_WIDE_EDGES_DEFAULT 3       /* gc_tuning.wide_edges of a process that does not set GCAST_WIDE_EDGES */
 #endif
 
+/* ---- GenCast's mesh transformer (csrc/attention.inc) ---------------------------------------------------------------
+ * The processor of the GenCast denoiser (weathernext1_gen/denoiser.py:330-335, weathernext1_gen/transformer.py,
+ * utils/sparse_transformer.py): blocks of  x += mha_final(attn(cond(LN(x))));  x += ffw_down(gelu(ffw_up(cond(LN(x))))).
+ * The Linear layers run as GC_MODE_LINEAR launches of gc_rowmlp; the entry points below are the rest.
+ *
+ * gc_attention   k-hop block-sparse multi-head attention, GC_ATTN_HEADS heads of GC_ATTN_HEAD columns:
+ *                  out[b, t, 128 h : 128 h + 128] = sum_T softmax_T(scale * q_t.k_T | mask[t, T]) v_T
+ *                q / k / v / out: [batch, n_rows, >= 512] row-major (row strides ld / ldo, batch stride n_rows rows),
+ *                16-byte aligned.  The mask is tiled in GC_ATTN_TILE x GC_ATTN_TILE blocks: query tile i (rows 64 i ..
+ *                64 i + 63) touches the key tiles tile_col[tile_ptr[i] .. tile_ptr[i + 1] - 1] (CSR, n_qtiles + 1
+ *                entries, n_qtiles = ceil(n_rows / 64)); tile_bits[64 t + r] bit c: query row r of the tile attends key
+ *                row c of key tile tile_col[t].  Every real query row needs at least one bit (the reference's masks hold
+ *                the self edges); rows past n_rows must have none.  Masked keys contribute exactly zero (the
+ *                reference's fill of -1e30).  prec GC_PREC_F32 (exact fp32 MFMA products) or GC_PREC_F16X3 (3 x fp16
+ *                split products for Q.K^T and P.V; a Q, K or V value with |x| > GC_F16X3_MAX sets *range_flag when
+ *                range_flag is not NULL -- the gc_rowmlp_desc.range_flag contract).  Softmax in fp32, online (running
+ *                max and sum), fixed summation order: bitwise repeatable.
+ * gc_ln_cond_rows  out[r] = LN(x[r]) * scale[b] + offset[b], b = r / rows_per_batch, rows of 512: hk.LayerNorm without
+ *                scale / offset (eps 1e-5, biased variance) + dense.LinearNormConditioning (utils/dense.py:360-393) with
+ *                the (1 + s_b) folded into `scale` [batch, 512] by the caller.  out may alias x.
+ * gc_gelu_rows   x[i] <- jax.nn.gelu(x[i]) (tanh approximation, jax's default), n floats (a multiple of 4) in place.
+ * gc_permute_rows  dst[b, r] = src[b, idx[r]] for 512-wide rows, r < n, b < batch; batch strides in ROWS, row strides
+ *                in floats.  (The caller's node order <-> the internal order of the tiles.)  dst must not alias src. */
+#define GC_ATTN_TILE 64
+#define GC_ATTN_HEAD 128
+#define GC_ATTN_HEADS 4
+int gc_attention(int prec, int batch, int n_rows, int n_qtiles, const int* tile_ptr, const int* tile_col,
+                 const unsigned long long* tile_bits, const float* q, const float* k, const float* v, int ld,
+                 float scale, float* out, int ldo, int* range_flag, void* stream);
+int gc_ln_cond_rows(int n_rows, int rows_per_batch, const float* x, const float* scale, const float* offset,
+                    float* out, void* stream);
+int gc_gelu_rows(long long n, float* x, void* stream);
+int gc_permute_rows(int n, int batch, const int* idx, const float* src, long long src_bstride, int ld_src, float* dst,
+                    long long dst_bstride, int ld_dst, void* stream);
+
 /* sizeof(gc_rowmlp_desc) for what == 0, sizeof(gc_op) for 1, sizeof(gc_advance_desc) for 2, sizeof(gc_model_desc) for 3, sizeof(gc_tuning) for 4, 0 otherwise:
  * lets a foreign-language binding verify its struct layout at load time. */
 size_t gc_abi_sizeof(int what);
